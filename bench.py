@@ -9,14 +9,19 @@ by independent IQ stream: rank r owns stream r on GPU r, no data-path collective
 the start/stop barrier and the max-over-ranks of the elapsed time).
 
 Headline workload (N = 1 and N > 1): cfg5 = BASELINE.json configs[4], the largest single-GPU configuration (the metric
-is quoted on no configuration; BASELINE.md calls cfg5 the HBM-roofline config).  At N = 1 the same line carries cfg2
-(configs[1]) and cfg3 (configs[2]) as "also" sub-records, each with its own roofline and parity check; at N > 1 it carries
-cfg3 on every GPU = cfg4 (configs[3]: N independent 61.44 MS/s streams, one per GPU).
+is quoted on no configuration; BASELINE.md calls cfg5 the HBM-roofline config).
 
-The timed region (W warm-up steps, then exactly K steps between barrier + synchronize) is REPEATED `--regions` times;
-`value` / `ms_per_step` are the median region, `timed_regions` lists first / min / median / max.
-Outside the timed regions every workload is checked against the CPU oracle (`parity_checked`): un-synchronised
-pipelined calls on the bench block, int16 PCM within +-1 LSB.
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs: set-up, W warm-up steps, ONE timed
+region of exactly K steps between barrier + synchronize (`value`, `ms_per_step`), the outputs of the last timed step if
+`--dump-outputs DIR` is given, and the line.
+
+`--full` adds everything else, as before: the timed region is REPEATED `--regions` times (default 25; `value` /
+`ms_per_step` are the median region, `timed_regions` lists first / min / median / max), kernel events and the roofline, the
+one-open-channel leg, the PCIe-inclusive host-buffer rates, the CPU baseline, and "also" sub-records -- at N = 1 cfg2
+(configs[1]) and cfg3 (configs[2]), each with its own roofline and parity check; at N > 1 cfg3 on every GPU = cfg4
+(configs[3]: N independent 61.44 MS/s streams, one per GPU).  Outside the timed regions every workload is checked against
+the CPU oracle (`parity_checked`): un-synchronised pipelined calls on the bench block, int16 PCM within +-1 LSB; a failed
+check fails the run.
 
 Prints ONE JSON line on rank 0 (see the driver contract in the task statement).
 """
@@ -43,6 +48,20 @@ HBM_PEAK_GBPS = 8000.0            # MI355X_MICROARCH.md: HBM3E 8 TB/s spec (6.3 
 KERNEL_SYMBOLS = ("profile slots name the kernels as a rocprofv3 trace does: k_fe_fast<MODE,N3,TAIL> = the specialised front end (MODE 1 = level 1 "
                   "of the two-level form; k_frontend<NT,SPT,MODE> for cascades it does not cover); audio FIR <hp> = k_fir_fft<4, DUAL> on "
                   "large blocks, k_fir_mfma4<...> otherwise")
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all (shared by the ranks)
+
+
+def dump_outputs(d, arrays, budget):
+    """--dump-outputs: each array as float32 d/<name>.npy.  One larger than `budget` bytes is replaced by a fixed sample of its
+    elements (seed 0, sorted flat indices): two builds run with the same arguments still compare element for element."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if a.nbytes > budget:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.size, budget // a.itemsize))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def _oracle_loop(fs, M, block_host, seconds_target, only_channel=-1):
@@ -227,9 +246,10 @@ def parity_check(ch, fs, M, iq, block, pcm_bufs, S, nblk, rot=1, sabotage=False)
             "seconds": round(time.perf_counter() - t0, 1)}
 
 
-def measure(name, args, rank, local_rank, world, dist, dev, headline):
-    """One workload: synth the block in HBM, warm up, time `regions` x K un-synchronised steps, per-kernel breakdown,
-    parity check.  Returns the record (rank 0) or None."""
+def measure(name, args, rank, local_rank, world, dist, dev, headline, dump=None):
+    """One workload: synth the block in HBM, warm up, time `regions` x K un-synchronised steps, write the last step's outputs
+    to `dump` if given; with --full also the per-kernel breakdown, the other legs and the parity check.  Returns the record
+    (rank 0) or None."""
     import torch
     from sdr_pmr446_amd import chain as pmr
     from sdr_pmr446_amd import multigpu
@@ -254,7 +274,7 @@ def measure(name, args, rank, local_rank, world, dist, dev, headline):
         raise SystemExit("--rotate must be a power of two")
     iq = pmr.synth_iq_device(rot * block, fs, M, stream_id=multigpu.stream_id_for_rank(rank), period_log2=lb + rot_log2,
                              device=local_rank)
-    nchk = max(1, args.parity_blocks)
+    nchk = max(1, args.parity_blocks) if args.full else 1
     pcm_bufs = [pmr.DeviceBuffer(M * S * 2, local_rank) for _ in range(nchk)]                # PCM stays in HBM
     pcm = pcm_bufs[0]
     pmr.device_synchronize()
@@ -263,12 +283,14 @@ def measure(name, args, rank, local_rank, world, dist, dev, headline):
         torch.cuda.synchronize()
         pmr.device_synchronize()
 
-    pos = [0, rot]                                    # [next block of the rotation, blocks in the rotation (1 = same block every step)]
+    pos = [0, rot, 0]                                 # [next block of the rotation, blocks in the rotation (1 = same block every step),
+                                                      #  frames of the last step]
 
     def step():
         b = pos[0] % pos[1]
         pos[0] += 1
-        return ch.process_block_device(iq.ptr + b * block * 8, block, d_pcm=pcm.ptr, stride=S)
+        pos[2] = ch.process_block_device(iq.ptr + b * block * 8, block, d_pcm=pcm.ptr, stride=S)
+        return pos[2]
 
     for _ in range(args.warmup):
         step()
@@ -285,7 +307,7 @@ def measure(name, args, rank, local_rank, world, dist, dev, headline):
     import math
     while math.gcd(event_every, args.steps) != 1:      # ... and coprime with the region length: the sampled launch must walk through
         event_every += 1                               # every position of a region (a region's first front end has the GPU to itself)
-    ch.profile_enable(0 if args.no_kernel_events else 1 + event_every)
+    ch.profile_enable(1 + event_every if args.full and not args.no_kernel_events else 0)
 
     def run():
         n = 0
@@ -301,14 +323,18 @@ def measure(name, args, rank, local_rank, world, dist, dev, headline):
         dts.append(dt)
     ch.profile_enable(0)
     prof_roof = ch.profile()
+    if dump:                                          # what a caller of the timed path receives from its last step: int16 PCM [M][frames]
+        import numpy as np
+        dump_outputs(dump, {"pcm" if rank == 0 else "pcm_rank%d" % rank:
+                            pcm.download(np.int16, M * S).reshape(M, S)[:, :pos[2]]}, DUMP_BYTES // world)
     # the same measurement on ONE block re-read every step (rounds 1-3's input), for the record: 5 regions
     dts_same = []
-    if rot > 1:
+    if args.full and rot > 1:
         pos[1] = 1
         dts_same = [multigpu.timed_region(run, dist, device_sync, sync_dev)[0] for _ in range(5)]
         pos[1] = rot
     breakdown_steps = 0
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         # separate pass, outside the timed region: every kernel, blocks NOT pipelined (uncontended kernel times)
         ch.set_overlap(False)
         ch.profile_reset()
@@ -323,7 +349,7 @@ def measure(name, args, rank, local_rank, world, dist, dev, headline):
     # the reference's own semantics (src/sdr_pmr446.c:876-877): one squelch-selected channel demodulated to audio
     from sdr_pmr446_amd import synth as _synth
     dts1 = []
-    if not args.no_one_open:
+    if args.full and not args.no_one_open:
         one = _synth.signal_channels(M, fs)[0]
         ch.set_channel_mask([one])
         for _ in range(args.warmup):
@@ -337,7 +363,7 @@ def measure(name, args, rank, local_rank, world, dist, dev, headline):
     # NUMA-local cores); the verdicts are AND-reduced over the gloo group.  Without this an 8-GPU run would return eight throughput
     # numbers and no evidence that device ordinals 1-7 compute the right thing (per-device hipSetDevice, table uploads, streams).
     par = None
-    if args.parity_blocks > 0:
+    if args.full and args.parity_blocks > 0:
         par = parity_check(ch, fs, M, iq, block, pcm_bufs, S, nchk if world == 1 else min(2, nchk), rot,
                            sabotage=args.test_fail_rank == rank)
         par["device"] = local_rank
@@ -398,11 +424,13 @@ def measure(name, args, rank, local_rank, world, dist, dev, headline):
                                  "note": "reference semantics (src/sdr_pmr446.c:876-877): channelizer + discriminator for all %d "
                                          "channels, audio FIR / PCM for the one open channel (pmr_chain_set_channel_mask)" % M},
         }
+        if not args.full:                                            # a plain run measured neither
+            del rec["roofline"], rec["one_open_channel"]
         if par is not None:
             rec["parity_checked"] = par
-        if headline and not args.no_host_io and world == 1:
+        if args.full and headline and not args.no_host_io and world == 1:
             rec["host_io"] = host_io(ch, iq, block, M, S)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # headline: ~16 s incl. one stream per core; sub-records: the single-core and one-channel figures only (~6 s each)
             rec["cpu_baseline"] = cpu_baseline(fs, M, 8.0 if headline else 4.0, multi=headline)
     ch.close()
@@ -508,16 +536,22 @@ def main():
     ap.add_argument("--steps", type=int, default=200, help="blocks per timed region (three blocks are in flight: a region "
                     "pays one pipeline fill/drain of ~0.17 ms, 6 %% of a 20-step region)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: repeated regions, kernel events and roofline, "
+                    "the other legs and workloads, the oracle parity check, the CPU baseline (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write the int16 PCM of the last one "
+                    "(channels x frames) as float32 DIR/pcm.npy (pcm_rank<r>.npy for rank r > 0); %d MB at most in all, a fixed "
+                    "seeded sample of a larger output" % (DUMP_BYTES >> 20))
     ap.add_argument("--workload", default=HEADLINE, choices=sorted(WORKLOADS))
-    ap.add_argument("--also", default=None, help="comma list of further workloads reported as sub-records "
+    ap.add_argument("--also", default=None, help="--full: comma list of further workloads reported as sub-records "
                                                  "(default at N = 1 with the default workload: cfg2,cfg3; 'none' disables)")
-    ap.add_argument("--regions", type=int, default=25, help="how often the timed K-step region is repeated")
-    ap.add_argument("--parity-blocks", type=int, default=4, help="blocks of the un-synchronised oracle check (0 = skip)")
+    ap.add_argument("--regions", type=int, default=None, help="how often the timed K-step region is repeated (default 1, "
+                                                              "25 with --full)")
+    ap.add_argument("--parity-blocks", type=int, default=4, help="--full: blocks of the un-synchronised oracle check (0 = skip)")
     ap.add_argument("--log2-block", type=int, default=None)
     ap.add_argument("--rotate", type=int, default=4, help="distinct device-resident blocks the timed steps rotate through (a power "
                     "of two; 1 = one block re-read every step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-one-open", action="store_true", help="skip the one-open-channel leg (profile runs: one kernel mix per trace)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-one-open", action="store_true", help="--full: skip the one-open-channel leg (profile runs: one kernel mix per trace)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) for real runs (falls back to gloo, and says so, if the "
                                                           "RCCL group does not come up); gloo lets two ranks share one GPU to "
                                                           "exercise the N > 1 code path on a 1-GPU box")
@@ -525,16 +559,18 @@ def main():
                     "fail there and the ranks must agree to fall back to gloo: the failure path of multigpu.init_dist, exercised on a 1-GPU box)")
     ap.add_argument("--host-io", action="store_true", help="(default since round 5; kept so that older command lines still parse)")
     ap.add_argument("--no-host-io", action="store_true",
-                    help="skip the PCIe-inclusive leg of the headline (host-buffer entry points on 2^22-sample calls, ~1 s)")
-    ap.add_argument("--no-kernel-events", action="store_true", help="skip per-kernel HIP events in the timed region")
+                    help="--full: skip the PCIe-inclusive leg of the headline (host-buffer entry points on 2^22-sample calls, ~1 s)")
+    ap.add_argument("--no-kernel-events", action="store_true", help="--full: skip per-kernel HIP events in the timed region")
     ap.add_argument("--ctcss", action="store_true", help="run with the CTCSS detector enabled (SURVEY s8 row f2) -- an A/B aid, "
                                                          "not the headline workload (the one_open_channel sub-record then is "
                                                          "the reference's mode: detector on the open channel only, :893)")
-    ap.add_argument("--test-fail-rank", type=int, default=-1, help="TEST ONLY: this rank falsifies the PCM it hands to its own oracle check, so "
+    ap.add_argument("--test-fail-rank", type=int, default=-1, help="TEST ONLY (--full): this rank falsifies the PCM it hands to its own oracle check, so "
                     "the job must print rank 0's line with that rank's verdict false and exit non-zero (tests/test_gpu_bench_ranks.py)")
     ap.add_argument("--allow-experiment", action="store_true", help="A/B tooling only: run on a library selected by PMR_LIBRARY or compiled with "
                     "-DPMR_EXPERIMENT; the line is then labelled as NOT a headline (metric prefixed, \"experiment\": true)")
     args = ap.parse_args()
+    if args.regions is None:
+        args.regions = 25 if args.full else 1
 
     # Which binary produces this line?  The headline is only ever taken from the in-tree product build: a library selected by
     # PMR_LIBRARY, or one compiled with the experiment gate open (csrc/pmr_experiment.h: timing-only hooks with wrong results), is
@@ -567,7 +603,9 @@ def main():
     affinity = multigpu.bind_to_gpu_numa(local_rank, min(world, ndev)) if world > 1 else None
     dist = multigpu.init_dist(args.dist_backend, dev)
 
-    if args.also is None:
+    if not args.full:
+        also = []
+    elif args.also is None:
         # N = 1: cfg2 and cfg3 ride along.  N > 1: cfg3 on every GPU IS BASELINE.json configs[3] ("cfg4": N independent
         # 61.44 MS/s streams, one per GPU) -- one timed region of it beside the headline
         also = [w for w in ("cfg2", "cfg3") if w != args.workload] if world == 1 else ["cfg3"]
@@ -576,7 +614,7 @@ def main():
     else:
         also = [w for w in args.also.split(",") if w in WORKLOADS and w != args.workload]
 
-    head = measure(args.workload, args, rank, local_rank, world, dist, dev, headline=True)
+    head = measure(args.workload, args, rank, local_rank, world, dist, dev, headline=True, dump=args.dump_outputs)
     subs = {}
     for w in also:
         r = measure(w, args, rank, local_rank, world, dist, dev, headline=False)

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_two_ranks_check_their_own_streams_and_report_in_one_line():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "PMR_DEBUG_POISON")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--workload", "cfg3", "--also", "none",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--dist-backend", "gloo", "--workload", "cfg3", "--also", "none",
                         "--log2-block", "24", "--steps", "6", "--warmup", "2", "--regions", "2", "--no-cpu-baseline", "--no-one-open"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-500:], r.stderr[-1500:])
@@ -32,7 +32,7 @@ def test_two_ranks_check_their_own_streams_and_report_in_one_line():
 
 def _run_bench(extra, timeout=1200):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "PMR_DEBUG_POISON")}
-    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dist-backend", "gloo", "--workload", "cfg3", "--also", "none",
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--dist-backend", "gloo", "--workload", "cfg3", "--also", "none",
                            "--no-cpu-baseline", "--no-one-open", "--no-kernel-events"] + extra, env=env, capture_output=True, text=True, timeout=timeout)
 
 

@@ -7,7 +7,7 @@ export PMR_OVERLAP=0
 B="--workload $W --also none --regions 1 --steps 3 --warmup 1 --no-cpu-baseline --no-host-io --no-kernel-events --parity-blocks 0"
 i=0
 for C in "$@"; do
-  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $O/p$i -- python3 $R/bench.py $B > /dev/null 2>&1
+  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $O/p$i -- python3 $R/bench.py --full $B > /dev/null 2>&1
   i=$((i+1))
 done
 PMC_KERNEL="$K" python3 - <<'PY'

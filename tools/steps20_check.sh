@@ -1,7 +1,7 @@
 for r in 1 2 3; do
 for W in cfg3 cfg2; do
   for E in "" "--no-kernel-events"; do
-    echo -n "$W bench.py $E: "; python3 bench.py --workload $W --also none --steps 20 --warmup 5 --no-cpu-baseline --no-host-io --parity-blocks 0 --no-one-open $E 2>/dev/null | python3 -c "
+    echo -n "$W bench.py $E: "; python3 bench.py --full --workload $W --also none --steps 20 --warmup 5 --no-cpu-baseline --no-host-io --parity-blocks 0 --no-one-open $E 2>/dev/null | python3 -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -10,7 +10,7 @@ for F in "$@"; do
     echo "BUILD FAILED for flags: $F"; grep -m3 -E "error" /tmp/variant_build.log; continue
   fi
   export PMR_LIBRARY=$PWD/build_ab/_variant/libpmr446_hip.so
-  python3 bench.py --allow-experiment --workload $W --also none --no-cpu-baseline --no-host-io --regions 5 --parity-blocks 0 2>&1 | python3 -c "
+  python3 bench.py --full --allow-experiment --workload $W --also none --no-cpu-baseline --no-host-io --regions 5 --parity-blocks 0 2>&1 | python3 -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

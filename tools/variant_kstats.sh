@@ -10,6 +10,6 @@ for F in "$@"; do
     echo "BUILD FAILED for flags: $F"; grep -m3 -E "error" /tmp/variant_build.log; continue
   fi
   export PMR_LIBRARY=$PWD/build_ab/_variant/libpmr446_hip.so
-  PMR_OVERLAP=0 bash tools/kstats.sh vk_tmp.txt --workload $W --also none --no-cpu-baseline --no-host-io --regions 2 --parity-blocks 0 --no-kernel-events --allow-experiment
+  PMR_OVERLAP=0 bash tools/kstats.sh vk_tmp.txt --full --workload $W --also none --no-cpu-baseline --no-host-io --regions 2 --parity-blocks 0 --no-kernel-events --allow-experiment
   head -6 gpurun_out/vk_tmp.txt
 done
